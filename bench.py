@@ -13,7 +13,17 @@ Weak scaling: each rank runs its own engine + stories; the join's
 all-gather is the cross-rank collective, so ranks stay in lockstep.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME]
+                       [--dump-outputs DIR] [--full]
 The driver launches N>1 via torch.distributed.run (one rank per GPU).
+
+A plain run does only what the headline figure needs: set up, warm up,
+time K steps, print one JSON result line.  `--dump-outputs DIR` also
+writes what the LAST timed step returned (every tensor payload of its
+step outputs plus the story output) as DIR/<name>.npy, float32/float64,
+at most 64 MB in all; inputs are seeded, so two builds run with the same
+arguments can be compared output for output.  `--full` is where any
+secondary measurement (other configs, baselines, per-kernel figures)
+belongs; the headline run has none today, so it changes nothing yet.
 """
 from __future__ import annotations
 
@@ -31,6 +41,7 @@ import torch  # noqa: E402
 from bobrapet_amd.engine import EngineConfig, RunEngine  # noqa: E402
 from bobrapet_amd.enums import Phase  # noqa: E402
 from bobrapet_amd.parallel import group  # noqa: E402
+from bobrapet_amd.storage import STORAGE_REF_KEY  # noqa: E402
 
 BRANCHES = 8
 EMBED_BATCH = 32
@@ -201,10 +212,82 @@ _R1_BASELINE = {
 }
 
 
-def run_one(eng: RunEngine, story_key: str, idx: int, rank: int, native=None, slot=None) -> dict:
+DUMP_CAP_BYTES = 64 * 1024 * 1024
+
+
+def _tensor_refs(doc, prefix: str):
+    """(name, marker) for every tensor `$storageRef` inside an output document."""
+    if isinstance(doc, dict):
+        meta = doc.get(STORAGE_REF_KEY)
+        if isinstance(meta, dict):
+            if meta.get("kind") == "tensor":
+                yield prefix, doc
+            return
+        for k in sorted(doc):
+            yield from _tensor_refs(doc[k], f"{prefix}.{k}")
+    elif isinstance(doc, list):
+        for i, v in enumerate(doc):
+            yield from _tensor_refs(v, f"{prefix}.{i}")
+
+
+def collect_outputs(eng: RunEngine, step_outputs: dict, story_output) -> dict:
+    """name -> numpy array (float32 tensors, float64 scalars) of what one
+    story run handed back: the tensor payloads of its step outputs and the
+    numeric fields of the story output.  Wall-clock fields (latencyMs) are
+    left out — they are measurements, not results."""
+    import numpy as np
+
+    arrays = {}
+    for step in sorted(step_outputs):
+        for name, marker in _tensor_refs(step_outputs[step], step):
+            t = eng.storage.hydrate(marker).detach()
+            if t.numel() * 4 > DUMP_CAP_BYTES:
+                # never stage more than the cap on the host: cut a seeded
+                # sample on the device first (write_outputs trims further)
+                pick = np.sort(np.random.default_rng(0).choice(
+                    t.numel(), DUMP_CAP_BYTES // 4, replace=False))
+                t = t.reshape(-1)[torch.from_numpy(pick).to(t.device)]
+            arrays[name] = t.to(device="cpu", dtype=torch.float32).numpy()
+    if isinstance(story_output, dict):
+        for k in sorted(story_output):
+            v = story_output[k]
+            if isinstance(v, (bool, int, float)):
+                arrays[f"output.{k}"] = np.asarray([v], dtype=np.float64)
+    return arrays
+
+
+def write_outputs(out_dir: str, arrays: dict) -> None:
+    """DIR/<name>.npy per array, at most DUMP_CAP_BYTES in all: an array
+    over its share of the cap is replaced by a fixed, seeded sample of its
+    flattened elements (same indices every run)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_CAP_BYTES // max(1, len(arrays))
+    for name, arr in arrays.items():
+        if arr.nbytes > share:
+            flat = arr.reshape(-1)
+            pick = np.random.default_rng(0).choice(
+                flat.size, share // arr.itemsize, replace=False
+            )
+            arr = flat[np.sort(pick)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+
+
+def run_one(eng: RunEngine, story_key: str, idx: int, rank: int, native=None, slot=None,
+            keep=None) -> dict:
+    """One story run; returns its per-step latencies.  `keep` (a dict) asks
+    for the run's outputs: they are collected before the run is reclaimed."""
     inputs = {"i": idx, "rank": rank, "slot": slot if slot is not None else 0}
     if native is not None:
-        status = native.run_story(story_key, inputs, timeout=600)
+        if keep is None:
+            status = native.run_story(story_key, inputs, timeout=600)
+        else:
+            # same submit + wait as run_story; the record (and the lane
+            # tensors it owns) is reclaimed by the caller after the dump
+            run_id = native.submit(story_key, inputs)
+            status = native.wait(run_id, 600)
+            keep["native"] = (run_id, status)
         if status["phase"] != "Succeeded":
             raise RuntimeError(f"native bench run failed: {status}")
         lat = {}
@@ -218,6 +301,8 @@ def run_one(eng: RunEngine, story_key: str, idx: int, rank: int, native=None, sl
         states = {k: (str(v.phase), v.message, str(v.error)) for k, v in run.step_states.items()}
         details = run.error.details if run.error is not None else None
         raise RuntimeError(f"bench run failed: {run.phase} {run.error} details={details} {states}")
+    if keep is not None:
+        keep["run"] = run
     lat = {}
     for name, st in run.step_states.items():
         if st.started_at and st.finished_at:
@@ -296,6 +381,7 @@ def run_stream_bench(eng, args, rank, world, n_gpus) -> int:
             time.sleep(0.001)
         group.barrier()
         elapsed = time.monotonic() - t0
+        leaf_seen = client.stream_stats(session)["leafPackets"]
         fin = client.finish_stream(session, timeout=60.0)
         if fin.get("phase") != "Finished":
             raise RuntimeError(f"stream bench failed: {fin}")
@@ -323,6 +409,7 @@ def run_stream_bench(eng, args, rank, world, n_gpus) -> int:
             time.sleep(0.001)
         group.barrier()
         elapsed = time.monotonic() - t0
+        leaf_seen = stream.leaf_packets
     if not use_grpc:
         run = stream.finish(timeout=30)
         if run.phase.value not in ("Finished",):
@@ -336,6 +423,16 @@ def run_stream_bench(eng, args, rank, world, n_gpus) -> int:
     if run is not None and "featurize" in run.step_states:
         out = run.step_states["featurize"].output or {}
         replays = out.get("graphReplays", 0)
+    if args.dump_outputs and rank == 0:
+        # a stream hands back per-stage summaries, not per-packet payloads:
+        # dump the tensors still referenced by the final stage outputs and
+        # the packet count that reached the leaf stage
+        arrays = collect_outputs(
+            eng,
+            {k: v.output for k, v in run.step_states.items()} if run is not None else {},
+            {"leafPackets": int(leaf_seen)},
+        )
+        write_outputs(args.dump_outputs, arrays)
     if rank == 0:
         line = {
             "metric": "StoryRuns/sec + p50 step latency, 8-way parallel Story",
@@ -380,6 +477,16 @@ def main() -> int:
     ap.add_argument(
         "--engine-impl", default="auto", choices=["auto", "python", "native"],
         help="DAG engine: the bobraccel C++ core (native) or the Python engine",
+    )
+    ap.add_argument(
+        "--dump-outputs", metavar="DIR", default=None,
+        help="after the timed steps, write what the last timed step returned "
+             "as DIR/<name>.npy (float32/float64, at most 64 MB in all)",
+    )
+    ap.add_argument(
+        "--full", action="store_true",
+        help="also run the secondary measurements (none today: a plain run "
+             "already does only what the headline figure needs)",
     )
     args = ap.parse_args()
     _defaults = {
@@ -485,6 +592,10 @@ def main() -> int:
         if inflight > 1:
             group.ensure_comm_slots(inflight)  # collective; same order on all ranks
 
+        # --dump-outputs: the last timed step (index steps-1) keeps its outputs
+        kept: dict = {}
+        keep_idx = args.steps - 1 if args.dump_outputs and rank == 0 else None
+
         def run_span(first: int, count: int) -> list:
             """Run `count` stories starting at `first`; W in-flight slot
             threads, slot s strictly sequential over indices s, s+W, ...
@@ -492,14 +603,16 @@ def main() -> int:
             if inflight <= 1:
                 lats: list = []
                 for i in range(first, first + count):
-                    lats.extend(run_one(eng, story_key, i, rank, native).values())
+                    lats.extend(run_one(eng, story_key, i, rank, native,
+                                        keep=kept if i == keep_idx else None).values())
                 return lats
             import concurrent.futures as cf
 
             def slot_main(slot: int) -> list:
                 out: list = []
                 for i in range(first + slot, first + count, inflight):
-                    out.extend(run_one(eng, story_key, i, rank, native, slot=slot).values())
+                    out.extend(run_one(eng, story_key, i, rank, native, slot=slot,
+                                       keep=kept if i == keep_idx else None).values())
                 return out
 
             with cf.ThreadPoolExecutor(max_workers=inflight) as ex:
@@ -528,6 +641,21 @@ def main() -> int:
         elapsed = time.monotonic() - t0
         if gc_was_enabled:
             gc.enable()
+
+        if args.dump_outputs and rank == 0:
+            if "native" in kept:
+                run_id, status = kept["native"]
+                arrays = collect_outputs(
+                    eng, {k: v.get("output") for k, v in status["steps"].items()},
+                    status.get("output"),
+                )
+                native.engine.gc_run(run_id)
+            else:
+                run = kept["run"]
+                arrays = collect_outputs(
+                    eng, {k: v.output for k, v in run.step_states.items()}, run.output
+                )
+            write_outputs(args.dump_outputs, arrays)
 
         elapsed_max = group.max_over_ranks(
             elapsed, device="cpu" if not has_gpu else None

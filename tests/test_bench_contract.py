@@ -42,6 +42,75 @@ def test_bench_default_single_rank():
     assert line["value"] > 0
 
 
+def _bench_dump(out_dir, *extra):
+    env = dict(os.environ)
+    env["BOBRA_BENCH_NO_CPU_FALLBACK"] = "1"  # the real parallel8 story
+    out = subprocess.run(
+        [sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1",
+         "--dump-outputs", str(out_dir), *extra],
+        cwd=REPO, env=env, capture_output=True, text=True, timeout=180,
+    )
+    assert out.returncode == 0, out.stderr[-2000:]
+    return json.loads(out.stdout.strip().splitlines()[-1])
+
+
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes what the last timed step returned, identically
+    from run to run; --full leaves the headline line's fields in place."""
+    import numpy as np
+
+    plain = _bench_dump(tmp_path / "a")
+    full = _bench_dump(tmp_path / "b", "--full")
+    for line in (plain, full):
+        assert line["steps"] == 3 and line["warmup"] == 1
+        assert line["ms_per_step"] > 0
+        assert line["value"] == pytest.approx(1000.0 / line["ms_per_step"], rel=1e-2)
+        assert line["config"]["bench_config"] == "parallel8"
+    assert {k: type(v) for k, v in plain.items()} == {k: type(v) for k, v in full.items()}
+
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "b").iterdir())
+    assert "join.joined.npy" in names and "output.rows.npy" in names
+    total = 0
+    for name in names:
+        a = np.load(tmp_path / "a" / name)
+        b = np.load(tmp_path / "b" / name)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        assert np.array_equal(a, b), name  # seeded inputs: same arrays every run
+        assert np.isfinite(a).all(), name
+        total += a.nbytes
+    assert total <= 64 * 1024 * 1024
+
+    joined = np.load(tmp_path / "a" / "join.joined.npy")
+    assert joined.shape == (8 * 32, 4096)
+    assert np.load(tmp_path / "a" / "output.rows.npy").tolist() == [256.0]
+    branches = [np.load(tmp_path / "a" / f"fanout.branches.b{i}.embeddings.npy")
+                for i in range(8)]
+    assert np.array_equal(joined, np.concatenate(branches, axis=0))
+    # embed-pool output rows are L2-normalized (bf16 storage)
+    assert np.allclose(np.linalg.norm(joined, axis=1), 1.0, atol=2e-2)
+
+
+def test_bench_dump_sampling_cap(tmp_path):
+    """An output over its share of the 64 MB cap is stored as a fixed,
+    seeded sample of its elements."""
+    import numpy as np
+
+    sys.path.insert(0, REPO)
+    import bench
+
+    big = np.arange(10 * 1024 * 1024, dtype=np.float64)  # 80 MB, every value exact
+    small = np.ones(7, dtype=np.float64)
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), {"big": big, "small": small})
+    a = np.load(tmp_path / "a" / "big.npy")
+    assert a.nbytes + small.nbytes <= bench.DUMP_CAP_BYTES
+    assert a.size == bench.DUMP_CAP_BYTES // 2 // 8
+    assert np.array_equal(a, np.load(tmp_path / "b" / "big.npy"))
+    assert np.all(np.diff(a) > 0)  # distinct source elements, in order
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), small)
+
+
 def _rank_main(rank: int, world: int, port: int, q) -> None:
     os.environ.update(
         {
@@ -150,6 +219,9 @@ def test_bench_parallel8_pipelined_two_ranks():
     port = _free_port()
     env = dict(os.environ)
     env.update({"BOBRA_BENCH_NO_CPU_FALLBACK": "1", "BOBRA_BENCH_INFLIGHT": "4"})
+    # the rehearsal is gloo on CPU: hide the GPUs, or two ranks would ask
+    # for two devices on a box that may have one
+    env["HIP_VISIBLE_DEVICES"] = "-1"
     out = subprocess.run(
         [
             sys.executable, "-m", "torch.distributed.run",

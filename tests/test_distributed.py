@@ -390,6 +390,9 @@ def _sp_engram_rank(rank: int, world: int, port: int, q):
             "LOCAL_RANK": str(rank),
             "MASTER_ADDR": "127.0.0.1",
             "MASTER_PORT": str(port),
+            # a CPU test (gloo, fp32 CPU reference): on a box with fewer
+            # GPUs than ranks the engram must not land on a shared GPU
+            "HIP_VISIBLE_DEVICES": "-1",
         }
     )
     try:
